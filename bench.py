@@ -1,6 +1,7 @@
 """Headline benchmark: per-channel int8 QDQ of a 4096 x 4096 bf16 weight on MI355X.
 
   python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run)
+                  [--dump-outputs DIR]                 (the last timed step's output, sampled rows, as .npy)
 
 One "step" = one pass of the hot path over one weight: sbq_quant_perchannel_forward
 (bf16 in -> bf16 out, per-channel symmetric int8, scales from the minmax observer), called
@@ -18,6 +19,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -26,6 +28,7 @@ if ROOT not in sys.path:
 
 ROWS = COLS = 4096
 NBUF = 12
+DUMP_ROWS = 2048  # --dump-outputs: half of the output's rows (32 MiB as float32; all of them would be 64 MiB)
 QMIN, QMAX = -128, 127
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 BYTES_PER_ELEM = 4  # algorithmic: 2 B read + 2 B written (bf16 -> bf16), SURVEY.md 8(d)
@@ -90,7 +93,12 @@ def main():
                          "(tools/reference_cpu_baseline.py, kind 'reference'); without one, oracle/torch_port.py (kind 'port')")
     ap.add_argument("--quick", action="store_true",
                     help="headline + multi-GPU plumbing only: no config legs, no CPU baseline (tests/test_gpu_bench_n2.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/qdq_output.npy (rank 0): %d of its %d output rows, "
+                         "a fixed seeded sample, as float32" % (DUMP_ROWS, ROWS))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` started like the N = 1 command: become the launcher the contract describes
@@ -183,6 +191,12 @@ def main():
         gates = BC.headline_gates(ctx)
         parity = gates["all"]
         assert parity, "timed kernel does not match the oracle: %r" % (gates,)
+    # --dump-outputs: the sampled rows of the last timed step's output are gathered on the device right after the timed
+    # region (the legs after it write into the same output buffers) and written to disk once the kernel windows are done
+    dump = None
+    if args.dump_outputs and rank == 0:
+        rows = torch.randperm(ROWS, generator=torch.Generator().manual_seed(0))[:DUMP_ROWS].sort().values
+        dump = (rows.to(dev), torch.empty(DUMP_ROWS, COLS, dtype=torch.bfloat16, device=dev))
 
     # ---- timed region ------------------------------------------------------------------------
     # K direct C-ABI launches on the current stream.  (Replaying the same launches from a
@@ -248,6 +262,8 @@ def main():
         step(i)
     sync_all()
     t1 = time.perf_counter()
+    if dump is not None:
+        torch.index_select(ys[(args.steps - 1) % NBUF], 0, dump[0], out=dump[1])
     wall = t1 - t0
     kern_us_timed = wall * 1e6 / args.steps  # the timed region itself: launch + synchronisation latency included
     # The kernel's duration for the roofline: NOT the K timed launches alone (K = 20 is a 0.25 ms sample) but windows
@@ -257,6 +273,9 @@ def main():
     post = [window(during=lambda: clocks.update(sample_clocks(dev_index)))]
     post += [window() for _ in range(7)]
     gc.enable()
+    if dump is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "qdq_output.npy"), dump[1].cpu().float().numpy())
     around = sorted(windows[-4:] + post)
     kern_us = 0.5 * (around[(len(around) - 1) // 2] + around[len(around) // 2])  # median
     if world > 1:

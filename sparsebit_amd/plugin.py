@@ -20,8 +20,8 @@ unmodified on top of the HIP kernels:
     reference quantizers that stay, e.g. adaround / quadapter, which call STE.apply)
 
 What makes this a drop-in rather than a registry swap (each point is exercised by
-tests/test_plugin_reference.py against the real reference and by tests/test_gpu_plugin.py against a
-reference-shaped harness on the GPU box):
+tests/test_gpu_plugin.py against a reference-shaped harness on the GPU box; the registry and native-module
+swap by tests/test_host_cpu.py against a package laid out like the reference's):
   * the reference hands quantizers ITS enum members -- `TARGET = (QuantTarget.FEATURE,)`,
     `set_backend(Backend.VIRTUAL)` (modules/base.py:36-45, common.py:5-35) -- and
     sparsebit_amd.common's enums compare and hash by name, so `fake_quant_factory[backend]`,

@@ -1,12 +1,12 @@
-"""The reference-side drop-in on the GPU box, where /root/reference does not exist.
+"""The reference-side drop-in, without the reference (it is not part of this repository).
 
 A reference-SHAPED harness stands in for the reference: its own `Backend` / `QuantTarget` enum classes
 (sparsebit/quantization/common.py:5-35), its own `Quantizer` / `Observer` base classes, a QuantOpr
 look-alike whose `build_quantizer` sets TARGET and the backend with THOSE enums
 (modules/base.py:36-45), and a model whose `export_onnx` finds quantizers with `isinstance(m, Quantizer)`
 against THAT base (quant_model.py:236,256).  The classes handed to it come from the same derivation
-plugin.install() performs (`plugin._derive`).  tests/test_plugin_reference.py runs the real reference
-through the same mechanics on the CPU container; here the kernels actually execute.
+plugin.install() performs (`plugin._derive`); tests/test_host_cpu.py checks install() itself on a package laid out
+like the reference's.  Here the kernels actually execute.
 
 The numbers: tests/golden/calib_golden.npz holds what the reference's own CalibrationRunner computed on the
 CPU for this operator chain (tests/golden/gen_calib_golden.py), in both asym modes.

@@ -88,7 +88,7 @@ def test_no_cpu_fallback_in_product_path():
         ops.fake_quant(torch.randn(4, 8), torch.ones(4), torch.zeros(4), -128, 127)
     with pytest.raises(lib.SbqError):
         ops.channel_stats(torch.randn(4, 8))
-    q = build_quantizer(quantizer_config("per-tensor-symmetric", 8))
+    q = build_quantizer(quantizer_config("per-tensor-symmetric", 8)).cpu()  # host qparams even where a GPU is visible
     q.enable_quant()
     q.backend = __import__("sparsebit_amd.common", fromlist=["Backend"]).Backend.VIRTUAL
     with pytest.raises(lib.SbqError):
@@ -170,36 +170,193 @@ def test_export_branch_stays_on_torch_builtins():
     assert torch.equal(y, want)
 
 
-def test_plugin_installs_into_reference_when_importable():
-    """Only where /root/reference exists (authoring container): registry + native-module swap."""
-    ref = "/root/reference"
-    if not os.path.isdir(ref):
-        pytest.skip("reference tree not present on this box")
-    code = r'''
-import sys, types, os
+# The modules of the reference's `sparsebit` package that plugin.install() reaches into, reduced to what it touches there
+# (quantization/quantizers/__init__.py, quant_tensor.py, observers/__init__.py, common.py, quant_model.py,
+# sparse/sparsers/__init__.py, sparse/sparse_model.py): the registries, the base classes whose __init__ an installed class
+# must never run, the native-module slot, the registry-driven builders, QuantModel's calibration entry points and
+# SparseModel's per-layer calc_params loop.  Written to a temporary directory by the tests: the reference itself is not
+# part of this repository.
+_REFERENCE_SHAPED_PACKAGE = {
+    "sparsebit/__init__.py": "",
+    "sparsebit/quantization/__init__.py": "",
+    "sparsebit/quantization/common.py": """
+from enum import Enum
+
+
+class QuantTarget(Enum):
+    WEIGHT = 0
+    FEATURE = 1
+""",
+    "sparsebit/quantization/quantizers/__init__.py": """
+import torch.nn as nn
+
+from . import quant_tensor
+
+
+class Quantizer(nn.Module):
+    def __init__(self, config):
+        raise AssertionError("the reference base's __init__ must not run for an installed class")
+
+
+QUANTIZERS_MAP = {"uniform": Quantizer}
+
+
+def build_quantizer(cfg):
+    return QUANTIZERS_MAP[cfg.QUANTIZER.TYPE.lower()](cfg)
+""",
+    "sparsebit/quantization/quantizers/quant_tensor.py": "fake_quant_kernel = None\n",
+    "sparsebit/quantization/observers/__init__.py": """
+import torch.nn as nn
+
+
+class Observer(nn.Module):
+    def __init__(self, config, qdesc):
+        raise AssertionError("the reference base's __init__ must not run for an installed class")
+
+
+OBSERVERS_MAP = {"minmax": Observer, "percentile": Observer}
+""",
+    "sparsebit/quantization/quant_model.py": """
+import torch.nn as nn
+
+
+class QuantModel(nn.Module):
+    def __init__(self, model):
+        super().__init__()
+        self.model = model
+        self.device = "cpu"
+
+    def prepare_calibration(self):
+        self.calibration_runner = "reference"
+
+    def calc_qparams(self, asym=False, w_quant=False, a_quant=False):
+        return "reference"
+""",
+    "sparsebit/sparse/__init__.py": "",
+    "sparsebit/sparse/sparsers/__init__.py": """
+import torch.nn as nn
+
+
+class Sparser(nn.Module):
+    def __init__(self, config, opr=None):
+        raise AssertionError("the reference base's __init__ must not run for an installed class")
+
+
+SPARSERS_MAP = {"l1norm": Sparser}
+
+
+def build_sparser(config, opr=None):
+    return SPARSERS_MAP[config.SPARSER.STRATEGY.lower()](config, opr=opr)
+""",
+    "sparsebit/sparse/sparse_model.py": """
+class SparseModel:
+    def __init__(self, model):
+        self.model = model
+
+    def calc_params(self):
+        for m in self.model.modules():
+            if getattr(m, "sparser", None) is not None:
+                m.mask = m.sparser.calc_mask(m.weight)
+""",
+}
+
+_INSTALLED_MAPS = ("['uniform', 'lsq', 'lsq+', 'pact', 'dorefa']", "['minmax', 'mse', 'percentile', 'moving_average', 'aciq']")
+
+
+def _run_against_reference_shaped_package(tmp_path, body):
+    """Runs `body` in a GPU-less subprocess with the stand-in package importable as `sparsebit`; -> its output."""
+    for rel, src in _REFERENCE_SHAPED_PACKAGE.items():
+        path = tmp_path / rel
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text(src)
+    code = r"""
+import sys, os
 sys.path.insert(0, os.path.join(%r, "tests", "golden"))
 import gen_golden
-gen_golden.install_stubs()
 sys.path.insert(0, %r)
 import sparsebit.quantization.quantizers as rq, sparsebit.quantization.observers as ro
 import sparsebit.quantization.quantizers.quant_tensor as rqt
+import sparsebit.quantization.quant_model as rqm
+import sparsebit.sparse.sparsers as rs, sparsebit.sparse.sparse_model as rsm
 sys.path.insert(0, %r)
-import sparsebit_amd.plugin as plugin, sparsebit_amd.fake_quant as fq
+import torch, torch.nn as nn
+import sparsebit_amd.plugin as plugin
+""" % (ROOT, str(tmp_path), ROOT) + body
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
+    r = subprocess.run([sys.executable, "-c", code], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env)
+    return r.stdout
+
+
+def test_plugin_installs_into_reference_shaped_package(tmp_path):
+    """plugin.install() on a package laid out like the reference's: registry + native-module swap, the l1norm sparser
+    derived from the foreign base (built through the foreign build_sparser without running that base's __init__) and
+    SparseModel.calc_params routed; calibration is left to the reference unless asked for."""
+    out = _run_against_reference_shaped_package(tmp_path, r"""
+import sparsebit_amd.fake_quant as fq
+from sparsebit_amd.config import sparser_config
+reference_prepare = rqm.QuantModel.prepare_calibration
 info = plugin.install()
+assert info == {"fake_quant_kernel": True, "quantizers": %s, "observers": %s,
+                "sparsers": ["l1norm", "calc_params:model-wide"], "calibrate": None}, info
 assert rqt.fake_quant_kernel is fq
 assert rq.QUANTIZERS_MAP["uniform"].__module__.startswith("sparsebit_amd")
 assert ro.OBSERVERS_MAP["percentile"].__module__.startswith("sparsebit_amd")
-from sparsebit.quantization.common import QuantTarget
 cfg = gen_golden.qcfg("per-channel-symmetric", 8)
 q = rq.build_quantizer(cfg)
 assert type(q).__module__ == "sparsebit_amd.quantizers.uniform", type(q)
+assert isinstance(q, rq.Quantizer) and isinstance(q.observer, ro.Observer)
 for n in ("quant_pertensor_forward","quant_perchannel_forward","quant_pertensor_backward","quant_perchannel_backward"):
     assert callable(getattr(rqt.fake_quant_kernel, n))
-print("PLUGIN_OK", info)
-''' % (ROOT, ref, ROOT)
-    env = dict(os.environ, HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
-    r = subprocess.run([sys.executable, "-c", code], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env)
-    assert "PLUGIN_OK" in r.stdout, r.stdout
+# the sparser: derived from the foreign base, built through the foreign builder, configured by the sparsebit_amd side
+lin = nn.Linear(8, 4)
+sp = rs.build_sparser(sparser_config(0.0), opr=lin)
+assert type(sp).__module__ == "sparsebit_amd.sparsers.l1norm", type(sp)
+assert isinstance(sp, rs.Sparser) and (sp.type, sp.strategy, sp.ratio, sp.opr) == ("unstructed", "l1norm", 0.0, lin)
+# SparseModel.calc_params: wrapped once, and the reference's own loop still runs inside the wrapper
+assert rsm.SparseModel.calc_params._sbq_grouped
+lin.sparser = sp
+rsm.SparseModel(nn.Sequential(lin)).calc_params()
+assert torch.equal(lin.mask, torch.ones_like(lin.weight))
+assert rqm.QuantModel.prepare_calibration is reference_prepare
+print("PLUGIN_OK")
+""" % _INSTALLED_MAPS)
+    assert "PLUGIN_OK" in out, out
+
+
+def test_plugin_routes_reference_shaped_calibration_to_the_device(tmp_path):
+    """install(calibrate="device") on a package laid out like the reference's: QuantModel.prepare_calibration installs
+    a DeviceCalibrator whose hooks hand the caller's forwards to the observers (without a GPU: to the library's device
+    check), and calc_qparams finishes on it."""
+    out = _run_against_reference_shaped_package(tmp_path, r"""
+from sparsebit_amd.calibration import DeviceCalibrator
+from sparsebit_amd.lib import SbqError
+info = plugin.install(calibrate="device")
+assert info["calibrate"] == "device" and info["sparsers"] == ["l1norm", "calc_params:model-wide"], info
+lin = nn.Linear(8, 4)
+lin.input_quantizer = rq.build_quantizer(gen_golden.qcfg("per-tensor-affine", 8, target_weight=False))
+lin.input_quantizer.enable_quant()
+qm = rqm.QuantModel(nn.Sequential(lin))
+qm.prepare_calibration()
+runner = qm.calibration_runner
+assert type(runner) is DeviceCalibrator, type(runner)
+assert [m for _, m in runner.oprs] == [lin] and len(runner._handles) == 1
+assert not lin.input_quantizer.use_quant and not qm.training
+try:  # the DeviceCalibrator's forward-pre hook hands the batch to the observer on the device
+    qm.model(torch.randn(2, 8))
+except SbqError as e:
+    assert "MI355X only" in str(e), e
+else:
+    raise AssertionError("the calibration forward did not reach the device")
+try:  # finished by the DeviceCalibrator: the observer holds no batch (the forward above never reached it)
+    qm.calc_qparams()
+except AssertionError as e:
+    assert "No data cached" in str(e), e
+else:
+    raise AssertionError("calc_qparams did not finish on the DeviceCalibrator")
+assert runner._handles is None and lin.input_quantizer.use_quant  # hooks removed, switches restored
+print("PLUGIN_OK")
+""")
+    assert "PLUGIN_OK" in out, out
 
 
 def test_gptq_pack_matches_reference_golden(golden):
@@ -384,6 +541,7 @@ def test_lsq_export_branch_builds_constants_without_a_host_round_trip():
     from sparsebit_amd.quantizers import build_quantizer
 
     q = build_quantizer(quantizer_config("per-channel-symmetric", 4, "lsq"))
+    q.device = torch.device("cpu")  # the export copies go to q.device: keep them on the host even where a GPU is visible
     q.set_backend(Backend.ONNXRUNTIME)
     q.dims = 2
     q.scale = torch.nn.Parameter(q._broadcast_qparams(torch.tensor([-0.1, 0.2, 0.05])))
